@@ -21,6 +21,11 @@ that axis (default 1 over dp: sharded optimizer states; 3 = ZeRO-3 per-block par
 composable with ``--pp`` / ``--tp`` — BASELINE config 5 is ``--model gpt3-13b --pp 2
 --sharding-degree 4 --sharding 3`` on 8 GPUs; ``--offload 1`` keeps its optimizer states on the host).
 Weak scaling: the per-GPU micro batch is fixed as N grows.
+
+A plain run does only that: set up, warm up, time the K steps, print the line. ``--dump-outputs DIR``
+then writes the last timed step's loss and a seeded sample of the updated parameters as ``.npy``
+(weights, token ids and dropout masks are seeded, so two builds can be compared output for output).
+``--full`` is reserved for measurements beyond the headline figure; none exist today.
 """
 from __future__ import annotations
 
@@ -34,6 +39,32 @@ import torch
 import torch.distributed as dist
 
 METRIC = "tokens/sec (node) GPT-3 1.3B Fleet hybrid-parallel at 1/2/4/8 MI355X"
+
+
+DUMP_PER_PARAM = 4096  # sampled elements per parameter: ~300 tensors x 16 KB, far below 64 MB
+
+
+def dump_outputs(out_dir, loss, net):
+    """What the last timed step handed back: its loss, and the parameters it updated. Each
+    parameter contributes its elements at indices drawn from a CPU generator with a fixed seed (all
+    of them when it has no more than DUMP_PER_PARAM), in ``named_parameters`` order, so two builds
+    run with the same arguments write arrays that compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    g = torch.Generator(device="cpu")
+    g.manual_seed(20240)
+    parts = []
+    for _, p in net.named_parameters():
+        flat_p = p.detach().reshape(-1)
+        n = flat_p.numel()
+        if n == 0:  # released by ZeRO-3: this rank holds no copy between steps
+            continue
+        if n > DUMP_PER_PARAM:
+            idx = torch.randint(0, n, (DUMP_PER_PARAM,), generator=g).to(flat_p.device)
+            flat_p = flat_p[idx]
+        parts.append(flat_p.float().cpu())
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
 
 
 def main():
@@ -68,6 +99,14 @@ def main():
                          "command without a GPU; not a performance number)")
     ap.add_argument("--tuned-gemm", type=int, default=0,
                     help="replay the in-tree TunableOp GEMM table (paddle_infer_amd/tuning)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32): loss.npy, and params.npy, a fixed seeded "
+                         "sample of every updated parameter this rank holds")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure; a plain "
+                         "run sets up, warms up, times --steps steps and prints the result line "
+                         "(there is nothing beyond that today)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -188,6 +227,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, net)
 
     tokens = args.steps * dp * shd * mb * S
     tps = tokens / elapsed

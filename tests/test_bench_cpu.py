@@ -48,6 +48,34 @@ def test_bench_multirank_contract(n, extra, par, gb):
     assert out["value"] > 0 and out["final_loss"] == out["final_loss"]
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs`` writes the last timed step's loss and parameter sample as float32 .npy;
+    a second run with the same arguments (``--full`` accepted) writes the same arrays."""
+    import numpy as np
+    outs = []
+    for i, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--device", "cpu", "--model", "gpt3-tiny", "--seq", "64", "--micro-batch", "2",
+               "--dump-outputs", str(d)] + extra
+        env = dict(os.environ, OMP_NUM_THREADS="1", PYTHONPATH=ROOT)
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["loss.npy", "params.npy"]
+        arrs = {n: np.load(d / n) for n in os.listdir(d)}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss.npy"].shape == (1,) and abs(float(arrs["loss.npy"][0]) - res["final_loss"]) < 1e-3
+        assert arrs["params.npy"].ndim == 1 and arrs["params.npy"].size > 1000
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        outs.append(arrs)
+    for n in outs[0]:
+        np.testing.assert_array_equal(outs[0][n], outs[1][n])
+
+
 def test_bench_gpt13b_pp2_sharding3_rehearsal():
     """BASELINE config 5's shape (GPT-3 13B, sharding stage 3 x pp 2) through the driver command,
     4 of its 40 layers at seq 64 so it fits a CPU rehearsal: real 13B widths (hidden 5120, 40
