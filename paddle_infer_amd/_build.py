@@ -147,7 +147,8 @@ def build_native(verbose: bool = True, jobs: int = 4) -> None:
     lib_srcs = [x for x in srcs if not x.endswith("pd_infer_run.cc")]
     objdir = os.path.join(OBJDIR, "native")
     os.makedirs(objdir, exist_ok=True)
-    hdr = _newest_header(NDIR)
+    # fast_ops.hip / gpu.hip include the kernel library's ABI headers (csrc/kernels/piamd_kernels.h)
+    hdr = max(_newest_header(NDIR), _newest_header(KDIR))
     todo, objs = [], []
     for src in lib_srcs:
         o = os.path.join(objdir, os.path.basename(src) + ".o")

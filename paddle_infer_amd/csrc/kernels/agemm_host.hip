@@ -109,8 +109,6 @@ PIAMD_EXPORT int piamd_agemm_load(const char* path) {
   return (int)hipModuleLoad(&g_mod, path);
 }
 
-PIAMD_EXPORT int piamd_agemm_loaded() { return g_mod != nullptr; }
-
 // C[M][N] (+)= op(A) · op(B), same contract as piamd_gemm_pipe:
 // trans_a: A stored [K][M] (else [M][K]); trans_b: B stored [N][K] (else [K][N]).
 // K % (64·ksplit) == 0 with K/ksplit ≥ 128; N % 4 == 0; leading dims % 8 == 0 and < 2^22;
@@ -123,12 +121,12 @@ PIAMD_EXPORT int piamd_agemm_loaded() { return g_mod != nullptr; }
 // colsum (nullable, epi == 2 only): the data-gradient epilogue also writes the column sums of C per
 // 128-row band into colsum f32 [ceil(M/128)][N] (the bias gradient of the activation's producer,
 // reduced over the bands by the caller: no separate pass over C).
-PIAMD_EXPORT int piamd_agemm2(const void* a, long long lda, int trans_a, const void* b, long long ldb,
-                              int trans_b, void* c, long long ldc, int c_f32, int accumulate, int M,
-                              int N, int K, int epi, int act, const void* bias, void* aux,
-                              long long ldaux, int ksplit, void* ws, int f16, int batch,
-                              long long sa, long long sb, long long sc, void* colsum,
-                              hipStream_t st) {
+PIAMD_EXPORT int piamd_agemm(const void* a, long long lda, int trans_a, const void* b, long long ldb,
+                             int trans_b, void* c, long long ldc, int c_f32, int accumulate, int M,
+                             int N, int K, int epi, int act, const void* bias, void* aux,
+                             long long ldaux, int ksplit, void* ws, int f16, int batch,
+                             long long sa, long long sb, long long sc, void* colsum,
+                             hipStream_t st) {
   const bool a_kc = !trans_a, b_kc = trans_b;
   if (batch < 1 || (batch > 1 && (ksplit != 1 || epi != 0 || sa < 0 || sb < 0 || sc <= 0)))
     return (int)hipErrorInvalidValue;
@@ -234,13 +232,4 @@ PIAMD_EXPORT int piamd_agemm2(const void* a, long long lda, int trans_a, const v
     hipLaunchKernelGGL(agemm_reduce_kernel<false>, dim3(grid), dim3(256), 0, st, (const float*)ws, ksplit,
                        M, N, c, ldc, c_f32, accumulate);
   return (int)hipGetLastError();
-}
-
-PIAMD_EXPORT int piamd_agemm(const void* a, long long lda, int trans_a, const void* b, long long ldb,
-                             int trans_b, void* c, long long ldc, int c_f32, int accumulate, int M,
-                             int N, int K, int epi, int act, const void* bias, void* aux,
-                             long long ldaux, int ksplit, void* ws, int f16, int batch,
-                             long long sa, long long sb, long long sc, hipStream_t st) {
-  return piamd_agemm2(a, lda, trans_a, b, ldb, trans_b, c, ldc, c_f32, accumulate, M, N, K, epi, act,
-                      bias, aux, ldaux, ksplit, ws, f16, batch, sa, sb, sc, nullptr, st);
 }

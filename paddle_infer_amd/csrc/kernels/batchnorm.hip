@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void bn_finalize(const float* __restrict__ par
 }
 
 // bn_finalize over channel-major partials part[(k·C + c)·P + b] (the conv forward's per-tile
-// statistics, piamd_conv2d_fwd2): each channel's P partials are contiguous.
+// statistics, piamd_conv2d_fwd): each channel's P partials are contiguous.
 __global__ __launch_bounds__(256) void bn_finalize_t(const float* __restrict__ part, int P, int C,
                                                      float eps, float momentum,
                                                      const float* __restrict__ gamma,
@@ -695,15 +695,15 @@ PIAMD_EXPORT int piamd_bn_set_parts(long long elems_per_block, int max_parts) {
 // place (momentum: Paddle convention); else the running statistics (mean/rstd still written).
 // ws: f32 workspace of ≥ 2·C + 3·2048·C floats. act: 0 none, 1 relu, 2 relu6.
 // nhwc requires C % 8 == 0 (vectorised path), C ≥ 256 or C | 256.
-// ss (nullable): f32 [2][C] receives the affine fold (scale, shift) for piamd_bn_bwd2's x-derived
+// ss (nullable): f32 [2][C] receives the affine fold (scale, shift) for piamd_bn_bwd's x-derived
 // ReLU mask; otherwise the fold lives in ws.
 // part_t (nullable, training only): precomputed channel-major statistics partials of x
-// ([3][C][P_t] count / mean / M2, piamd_conv2d_fwd2) — the statistics pass over x is skipped.
-PIAMD_EXPORT int piamd_bn_fwd3(int dtype, int nhwc, const void* x, const void* res, void* y, int N,
-                               int C, int S, const float* gamma, const float* beta,
-                               float* run_mean, float* run_var, float* mean, float* rstd,
-                               float momentum, float eps, int training, int act, float* ws, float* ss,
-                               const float* part_t, int P_t, hipStream_t st) {
+// ([3][C][P_t] count / mean / M2, piamd_conv2d_fwd) — the statistics pass over x is skipped.
+PIAMD_EXPORT int piamd_bn_fwd(int dtype, int nhwc, const void* x, const void* res, void* y, int N,
+                              int C, int S, const float* gamma, const float* beta,
+                              float* run_mean, float* run_var, float* mean, float* rstd,
+                              float momentum, float eps, int training, int act, float* ws, float* ss,
+                              const float* part_t, int P_t, hipStream_t st) {
   if (C < 1 || N < 1 || S < 1 || (nhwc && C % 8 && C < 256 && 256 % C) || (part_t && (!training || P_t < 1)))
     return (int)hipErrorInvalidValue;
   const long long M = (long long)N * S, total = M * C;
@@ -753,33 +753,15 @@ PIAMD_EXPORT int piamd_bn_fwd3(int dtype, int nhwc, const void* x, const void* r
   return (int)hipGetLastError();
 }
 
-PIAMD_EXPORT int piamd_bn_fwd2(int dtype, int nhwc, const void* x, const void* res, void* y, int N,
-                               int C, int S, const float* gamma, const float* beta,
-                               float* run_mean, float* run_var, float* mean, float* rstd,
-                               float momentum, float eps, int training, int act, float* ws, float* ss,
-                               hipStream_t st) {
-  return piamd_bn_fwd3(dtype, nhwc, x, res, y, N, C, S, gamma, beta, run_mean, run_var, mean, rstd,
-                       momentum, eps, training, act, ws, ss, nullptr, 0, st);
-}
-
-PIAMD_EXPORT int piamd_bn_fwd(int dtype, int nhwc, const void* x, const void* res, void* y, int N,
-                              int C, int S, const float* gamma, const float* beta,
-                              float* run_mean, float* run_var, float* mean, float* rstd,
-                              float momentum, float eps, int training, int act, float* ws,
-                              hipStream_t st) {
-  return piamd_bn_fwd2(dtype, nhwc, x, res, y, N, C, S, gamma, beta, run_mean, run_var, mean, rstd,
-                       momentum, eps, training, act, ws, nullptr, st);
-}
-
 // Backward. y = the forward OUTPUT (act' from it); dres (nullable) receives dz = ∂L/∂(bn + res).
 // training = 0: the statistics are constants (dx = γ·rstd·dz). dgamma / dbeta: f32 [C]
 // (nullable). ws: ≥ 3·C + 2·2048·C floats. ss (nullable): the forward's fold from
-// piamd_bn_fwd2 — with ReLU, no residual and NHWC C % 8 == 0 the mask is x·scale + shift > 0
+// piamd_bn_fwd — with ReLU, no residual and NHWC C % 8 == 0 the mask is x·scale + shift > 0
 // (the forward's own test) and y is not read.
-PIAMD_EXPORT int piamd_bn_bwd2(int dtype, int nhwc, const void* dy, const void* y, const void* x,
-                               void* dx, void* dres, int N, int C, int S, const float* gamma,
-                               const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                               int training, int act, float* ws, const float* ss, hipStream_t st) {
+PIAMD_EXPORT int piamd_bn_bwd(int dtype, int nhwc, const void* dy, const void* y, const void* x,
+                              void* dx, void* dres, int N, int C, int S, const float* gamma,
+                              const float* mean, const float* rstd, float* dgamma, float* dbeta,
+                              int training, int act, float* ws, const float* ss, hipStream_t st) {
   if (C < 1 || N < 1 || S < 1 || (nhwc && C % 8 && C < 256 && 256 % C))
     return (int)hipErrorInvalidValue;
   const float* msc = act == 1 && !dres && ss && nhwc && C % 8 == 0 ? ss : nullptr;
@@ -826,18 +808,10 @@ PIAMD_EXPORT int piamd_bn_bwd2(int dtype, int nhwc, const void* dy, const void* 
   return (int)hipGetLastError();
 }
 
-PIAMD_EXPORT int piamd_bn_bwd(int dtype, int nhwc, const void* dy, const void* y, const void* x,
-                              void* dx, void* dres, int N, int C, int S, const float* gamma,
-                              const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                              int training, int act, float* ws, hipStream_t st) {
-  return piamd_bn_bwd2(dtype, nhwc, dy, y, x, dx, dres, N, C, S, gamma, mean, rstd, dgamma, dbeta,
-                       training, act, ws, nullptr, st);
-}
-
 // ------------------------------------------------------------------- cross-rank (SyncBatchNorm)
 // Reference `phi/kernels/gpu/sync_batch_norm_kernel.cu:192` / `sync_batch_norm_utils.h`. The
 // framework's SyncBatchNorm runs these kernels around RCCL collectives issued from Python:
-//   fwd: local (count, mean, M2) per channel → all-gather over ranks → piamd_bn_fwd3 with the
+//   fwd: local (count, mean, M2) per channel → all-gather over ranks → piamd_bn_fwd with the
 //        gathered triples as channel-major partials (Welford merge across ranks: no E[x²]−E[x]²
 //        cancellation) → normalise + running statistics;
 //   bwd: local Σdz, Σdz·x̂ → all-reduce → dx from the global sums (dγ / dβ stay the local sums,

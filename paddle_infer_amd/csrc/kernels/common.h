@@ -6,12 +6,13 @@
 //     narrowing uses the hardware `v_cvt_pk_bf16_f32` (plain `__bf16` cast at -O3), which keeps NaN.
 //   * global loads are 16 B/lane (`u16x8`) wherever the row length allows (guide G13).
 //   * every exported launcher is `extern "C" int piamd_<name>(..., hipStream_t)` returning the
-//     hipError_t of the launch, so the Python side can raise loudly.
+//     hipError_t of the launch, so the Python side can raise loudly. A new entry point is declared
+//     in piamd_kernels.h and nowhere else: Python and the native engine read that header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define PIAMD_EXPORT extern "C" __attribute__((visibility("default")))
+#include "piamd_kernels.h"
 
 typedef unsigned short bf16_t;
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));

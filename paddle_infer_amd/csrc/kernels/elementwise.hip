@@ -356,7 +356,7 @@ PIAMD_EXPORT int piamd_bias_act_fwd(int dt, int act, const void* x, const void* 
   return (int)hipGetLastError();
 }
 
-PIAMD_EXPORT int piamd_bias_act_bwd_grid(int rows) {
+static int bias_act_bwd_grid(int rows) {
   int g = rows < 256 ? rows : 256;
   return g < 1 ? 1 : g;
 }
@@ -367,7 +367,7 @@ PIAMD_EXPORT int piamd_bias_act_bwd(int dt, int act, const void* dy, const void*
                                     int accumulate, hipStream_t stream) {
   if (rows == 0) return 0;
   if (N % 8) return (int)hipErrorInvalidValue;
-  const int G = piamd_bias_act_bwd_grid(rows);
+  const int G = bias_act_bwd_grid(rows);
   dim3 grid(G, (N / 8 + 255) / 256);
 #define BAB(A)                                                                                   \
   case A:                                                                                        \
@@ -459,7 +459,7 @@ __global__ void __launch_bounds__(256) transpose_bf16_kernel(const bf16_t* __res
   }
 }
 
-PIAMD_EXPORT int piamd_transpose_bf16(const void* src, void* dst, int R, int C,
+PIAMD_EXPORT int piamd_bf16_transpose(const void* src, void* dst, int R, int C,
                                       hipStream_t stream) {
   if (R == 0 || C == 0) return 0;
   if (R % 8 || C % 8) return (int)hipErrorInvalidValue;
@@ -500,8 +500,8 @@ __global__ void split3_f32_kernel(const float* __restrict__ src, long long ld, b
   }
 }
 
-PIAMD_EXPORT int piamd_split3_f32(const void* src, long long ld, void* dst, int R, int C, int Rp, int Cp,
-                                  int lo_mask, int axis, hipStream_t stream) {
+PIAMD_EXPORT int piamd_f32_split_hilo(const void* src, long long ld, void* dst, int R, int C, int Rp,
+                                      int Cp, int lo_mask, int axis, hipStream_t stream) {
   if (Rp == 0 || Cp == 0) return 0;
   if (Cp % 8 || Rp < R || Cp < C || (axis != 0 && axis != 1)) return (int)hipErrorInvalidValue;
   const long long n = (long long)Rp * (Cp / 8);

@@ -151,22 +151,12 @@ __global__ __launch_bounds__(256) void pos_bwd_kernel(const bf16_t* __restrict__
 
 }  // namespace
 
-// out [T][H] bf16 = W[ids - start] (zero outside [0, vlocal)) + P[pos] (P may be null; pos null →
-// t mod S). H % 8 == 0, 16-B aligned rows.
-PIAMD_EXPORT int piamd_embedding_fwd(const long long* ids, const void* w, long long start,
+// out [T][H] = W[ids - start] (zero outside [0, vlocal)) + P[pos] (P may be null; pos null →
+// t mod S). H % 8 == 0, 16-B aligned rows. Any element type (dtype 0 f32, 1 bf16, 2 fp16: weight,
+// position table and output alike).
+PIAMD_EXPORT int piamd_embedding_fwd(int dtype, const long long* ids, const void* w, long long start,
                                      int vlocal, const void* p, const long long* pos, int S,
                                      void* out, long long T, int H, hipStream_t st) {
-  if (H % 8 || T < 0 || (p && !pos && S < 1)) return (int)hipErrorInvalidValue;
-  if (T == 0) return 0;
-  hipLaunchKernelGGL(emb_fwd_kernel<1>, dim3(stride_grid(T * (H / 8), 256)), dim3(256), 0, st, ids, w,
-                     start, vlocal, p, pos, S, out, T, H);
-  return (int)hipGetLastError();
-}
-
-// Any element type (dtype 0 f32, 1 bf16, 2 fp16: weight, position table and output alike).
-PIAMD_EXPORT int piamd_embedding_fwd_dt(int dtype, const long long* ids, const void* w, long long start,
-                                        int vlocal, const void* p, const long long* pos, int S,
-                                        void* out, long long T, int H, hipStream_t st) {
   if (H % 8 || T < 0 || (p && !pos && S < 1) || dtype < 0 || dtype > 2) return (int)hipErrorInvalidValue;
   if (T == 0) return 0;
   const dim3 grid(stride_grid(T * (H / 8), 256));

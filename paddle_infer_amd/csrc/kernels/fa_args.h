@@ -1,6 +1,6 @@
 // Argument block of the flash-attention entry points (piamd_fa_fwd / piamd_fa_bwd). Shared by
 // the kernels (flash_attn.h), the Python binding (ops/_lib.py mirrors it with ctypes) and the
-// native predictor (csrc/native/fast_ops.hip).
+// native predictor (csrc/native/fast_ops.hip), all through piamd_kernels.h.
 #pragma once
 
 struct FaArgs {

@@ -896,10 +896,10 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const bf16_t* __restric
 // x [M][K] int8 row-major (ldx bytes), wq [N][K] int8 (ldw bytes); xs [M] per-row activation
 // scales (or null → xs_const), ws [N] per-channel weight scales; y [M][N] bf16. K % 128 == 0,
 // 16-byte aligned rows, N % 4 == 0.
-PIAMD_EXPORT int piamd_gemm_i8(const void* x, long long ldx, const void* wq, long long ldw,
-                               const float* xs, float xs_const, const float* ws, const void* bias,
-                               void* y, long long ldy, int M, int N, int K, int act,
-                               hipStream_t st) {
+PIAMD_EXPORT int piamd_int8_gemm(const void* x, long long ldx, const void* wq, long long ldw,
+                                 const float* xs, float xs_const, const float* ws,
+                                 const void* bias, void* y, long long ldy, int M, int N, int K,
+                                 int act, hipStream_t st) {
   if (K % 128 || N % 4 || M <= 0 || N <= 0 || ldx % 16 || ldw % 16) return (int)hipErrorInvalidValue;
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   hipLaunchKernelGGL(gemm_i8_kernel, dim3(tiles), dim3(NTHR), 0, st, (const signed char*)x, ldx,
@@ -946,12 +946,12 @@ static void conv_fwd_launch(int tile_n, bool sc, unsigned grid, hipStream_t st, 
 // dst_h > 0: y is an N × dst_h × dst_w × Kout tensor and this convolution's OH × OW outputs are
 // its phase (ph, pw) of stride (rs_h, rs_w): pixel (oh, ow) lands on (oh·rs_h + ph, ow·rs_w + pw)
 // (the strided data gradient's phases, written in place) — ksplit == 1.
-PIAMD_EXPORT int piamd_conv2d_fwd3(const void* x, const void* wt, const void* zero, void* y, int N,
-                                   int H, int W, int C, int OH, int OW, int R, int S, int st_h,
-                                   int st_w, int pad_h, int pad_w, int dil_h, int dil_w, int Kout,
-                                   int act, const void* bias, int tile_n, int ksplit, void* ws,
-                                   int flags, float* stats, int dst_h, int dst_w, int rs_h, int rs_w,
-                                   int ph, int pw, hipStream_t st) {
+PIAMD_EXPORT int piamd_conv2d_fwd(const void* x, const void* wt, const void* zero, void* y, int N,
+                                  int H, int W, int C, int OH, int OW, int R, int S, int st_h,
+                                  int st_w, int pad_h, int pad_w, int dil_h, int dil_w, int Kout,
+                                  int act, const void* bias, int tile_n, int ksplit, void* ws,
+                                  int flags, float* stats, int dst_h, int dst_w, int rs_h, int rs_w,
+                                  int ph, int pw, hipStream_t st) {
   const bool sc = C == 8;
   // flags bit 2: y += the convolution (16-bit y, ksplit == 1, no bias / activation / stats)
   const int f16 = flags & 1, yf32 = (flags >> 1) & 1, yacc = (flags >> 2) & 1;
@@ -990,24 +990,6 @@ PIAMD_EXPORT int piamd_conv2d_fwd3(const void* x, const void* wt, const void* ze
     else hipLaunchKernelGGL(conv_splitk_finish<false>, fg, dim3(256), 0, st, wsf, ksplit, MN, Kout, act, bb, (bf16_t*)y);
   }
   return (int)hipGetLastError();
-}
-
-PIAMD_EXPORT int piamd_conv2d_fwd(const void* x, const void* wt, const void* zero, void* y, int N,
-                                  int H, int W, int C, int OH, int OW, int R, int S, int st_h,
-                                  int st_w, int pad_h, int pad_w, int dil_h, int dil_w, int Kout,
-                                  int act, const void* bias, int tile_n, int ksplit, void* ws,
-                                  int flags, hipStream_t st) {
-  return piamd_conv2d_fwd3(x, wt, zero, y, N, H, W, C, OH, OW, R, S, st_h, st_w, pad_h, pad_w, dil_h,
-                           dil_w, Kout, act, bias, tile_n, ksplit, ws, flags, nullptr, 0, 0, 0, 0, 0, 0, st);
-}
-
-PIAMD_EXPORT int piamd_conv2d_fwd2(const void* x, const void* wt, const void* zero, void* y, int N,
-                                   int H, int W, int C, int OH, int OW, int R, int S, int st_h,
-                                   int st_w, int pad_h, int pad_w, int dil_h, int dil_w, int Kout,
-                                   int act, const void* bias, int tile_n, int ksplit, void* ws,
-                                   int flags, float* stats, hipStream_t st) {
-  return piamd_conv2d_fwd3(x, wt, zero, y, N, H, W, C, OH, OW, R, S, st_h, st_w, pad_h, pad_w, dil_h,
-                           dil_w, Kout, act, bias, tile_n, ksplit, ws, flags, stats, 0, 0, 0, 0, 0, 0, st);
 }
 
 // NHWC implicit-GEMM convolution weight gradient: x [N][H][W][C], dy [N][OH][OW][Kout] 16-bit

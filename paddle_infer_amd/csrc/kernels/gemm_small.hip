@@ -406,13 +406,13 @@ int sg_dispatch(const SgArgs& p, int mb, int nb, int wn, int ks, int depth, int*
 // ks == 1, alpha == 1; ln_stats (f32 [M][2], nullable): the (mean, rstd) of each raw A row out.
 // rln_stats (f32 [M][2]) + rln_g / rln_b (16-bit [N]), with resid: the residual is a raw row whose
 // LayerNorm its producer deferred — LN(resid) = (r − mean)·rstd·γ + β is added instead of r.
-PIAMD_EXPORT int piamd_small_gemm_ln(int f16, const void* a, long long lda, const void* b,
-                                     long long ldb, void* c, long long ldc, int c_f32, int M, int N,
-                                     int K, int mb, int nb, int wn, int depth, int ks, float alpha,
-                                     const void* bias, int act, const void* resid, long long ldr,
-                                     float* ws, int* cnt, const float* ln_c1, const float* ln_b2,
-                                     float ln_eps, float* ln_stats, const float* rln_stats,
-                                     const void* rln_g, const void* rln_b, hipStream_t st) {
+PIAMD_EXPORT int piamd_small_gemm(int f16, const void* a, long long lda, const void* b,
+                                  long long ldb, void* c, long long ldc, int c_f32, int M, int N,
+                                  int K, int mb, int nb, int wn, int depth, int ks, float alpha,
+                                  const void* bias, int act, const void* resid, long long ldr,
+                                  float* ws, int* cnt, const float* ln_c1, const float* ln_b2,
+                                  float ln_eps, float* ln_stats, const float* rln_stats,
+                                  const void* rln_g, const void* rln_b, hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 4 || lda % 8 || ldb % 8 || ldc % 4 || ks < 1 ||
       ks > K / 64 || (ks > 1 && !ws) || ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16)
     return (int)hipErrorInvalidValue;
@@ -438,14 +438,4 @@ PIAMD_EXPORT int piamd_small_gemm_ln(int f16, const void* a, long long lda, cons
     else hipLaunchKernelGGL(small_gemm_finish<false>, dim3(grid), dim3(256), 0, st, p, ks);
   }
   return (int)hipGetLastError();
-}
-
-PIAMD_EXPORT int piamd_small_gemm(int f16, const void* a, long long lda, const void* b, long long ldb,
-                                  void* c, long long ldc, int c_f32, int M, int N, int K, int mb,
-                                  int nb, int wn, int depth, int ks, float alpha, const void* bias,
-                                  int act, const void* resid, long long ldr, float* ws, int* cnt,
-                                  hipStream_t st) {
-  return piamd_small_gemm_ln(f16, a, lda, b, ldb, c, ldc, c_f32, M, N, K, mb, nb, wn, depth, ks,
-                             alpha, bias, act, resid, ldr, ws, cnt, nullptr, nullptr, 0.f, nullptr,
-                             nullptr, nullptr, nullptr, st);
 }

@@ -297,14 +297,9 @@ int bwd(const void* dy, const void* x, const float* gamma, const float* mean, co
 
 }  // namespace
 
-// Floats of workspace both entry points need: max(3·N·C, 2·N·C + 2·N·G).
-PIAMD_EXPORT long long piamd_group_norm_ws(int N, int C, int G) {
-  const long long a = 3LL * N * C, b = 2LL * N * C + 2LL * N * G;
-  return a > b ? a : b;
-}
-
 // dtype: 0 f32, 1 bf16, 2 fp16. x / y [N][C][HW] contiguous (16-B aligned), C % G == 0; gamma /
-// beta f32 [C] (nullable); mean / rstd f32 [N·G] out.
+// beta f32 [C] (nullable); mean / rstd f32 [N·G] out. ws (every entry point): f32 workspace of
+// max(3·N·C, 2·N·C + 2·N·G) floats.
 PIAMD_EXPORT int piamd_group_norm_fwd(int dtype, const void* x, void* y, const float* gamma,
                                       const float* beta, float* mean, float* rstd, float* ws, int N,
                                       int C, long long HW, int G, float eps, hipStream_t st) {

@@ -734,14 +734,14 @@ static void wo_launch(int bits, dim3 grid, hipStream_t st, const void* x, long l
 #undef WO_LAUNCH
 }
 
-// Extended form: ln_g/ln_b (nullable, bf16 [K]): y = act(LN(x)·Wᵀ·scale + bias) with the
+// ln_g/ln_b (nullable, bf16 [K]): y = act(LN(x)·Wᵀ·scale + bias) with the
 // LayerNorm (ε = eps) computed in the prologue — requires KS == 1, M ≤ 8, K % 512 == 0, K ≤ 2048;
 // resid (nullable, bf16 rows of pitch ldr): + resid[m, n] after the activation.
-PIAMD_EXPORT int piamd_wo_gemm_ex(int bits, const void* x, long long ldx, const void* wp,
-                                  const float* scale, const void* bias, void* y, long long ldy,
-                                  float* ws, int* cnt, int M, int N, int K, int KS, int act,
-                                  const void* ln_g, const void* ln_b, float eps, const void* resid,
-                                  long long ldr, hipStream_t st) {
+PIAMD_EXPORT int piamd_wo_gemm(int bits, const void* x, long long ldx, const void* wp,
+                               const float* scale, const void* bias, void* y, long long ldy,
+                               float* ws, int* cnt, int M, int N, int K, int KS, int act,
+                               const void* ln_g, const void* ln_b, float eps, const void* resid,
+                               long long ldr, hipStream_t st) {
   const int KB = bits == 16 ? 16 : (bits == 8 ? 32 : 64);
   if ((bits != 16 && bits != 8 && bits != 4) || N % 32 || K % KB || KS < 1 ||
       (KS > 1 && !ws) || M < 1 || (ln_g && (!ln_b || KS != 1 || K % 512 || K > 2048 || M > 8)))
@@ -753,14 +753,6 @@ PIAMD_EXPORT int piamd_wo_gemm_ex(int bits, const void* x, long long ldx, const 
                        st, ws, KS, scale, (const bf16_t*)bias, (bf16_t*)y, ldy, M, N, act,
                        (const bf16_t*)resid, ldr);
   return (int)hipGetLastError();
-}
-
-PIAMD_EXPORT int piamd_wo_gemm(int bits, const void* x, long long ldx, const void* wp,
-                               const float* scale, const void* bias, void* y, long long ldy,
-                               float* ws, int* cnt, int M, int N, int K, int KS, int act,
-                               hipStream_t st) {
-  return piamd_wo_gemm_ex(bits, x, ldx, wp, scale, bias, y, ldy, ws, cnt, M, N, K, KS, act,
-                          nullptr, nullptr, 0.f, nullptr, 0, st);
 }
 
 // Grouped weight-only expert GEMM (the decode / small-batch MoE path of

@@ -980,7 +980,7 @@ PIAMD_EXPORT int piamd_colsum(int dtype, const void* x, void* out, float* part, 
 }
 
 // out[N] (+)= Σ_g part[g][N] (f32 partial rows — e.g. the column-sum planes the assembly GEMM's
-// dact epilogue writes, piamd_agemm2 colsum): the bias gradient without a pass over the activation.
+// dact epilogue writes, piamd_agemm colsum): the bias gradient without a pass over the activation.
 PIAMD_EXPORT int piamd_colsum_parts(int dtype, const float* part, int G, int N, void* out, int accumulate,
                                     hipStream_t stream) {
   if (G <= 0 || N <= 0) return 0;

@@ -5,7 +5,7 @@
 // * GEMMs: a port of ops/gemm.py `gemm_nt` — the skinny MFMA kernel (piamd_small_gemm, tuned
 //   configs + heuristic) for few rows, the assembly GEMM (piamd_agemm: persistent, split-K, fused
 //   bias / bias+GELU(erf|tanh) / bias+ReLU epilogues) otherwise. Weights stored [in, out] are
-//   transposed once to K-contiguous [out, in] copies (piamd_transpose_bf16) and cached.
+//   transposed once to K-contiguous [out, in] copies (piamd_bf16_transpose) and cached.
 // * Fused transformer ops of an IR-optimised program (the Python Predictor's passes, saved with
 //   `Predictor.save_optimized_model`): multihead_matmul (QKV GEMM + bias, packed flash attention
 //   with the BiasQK mask), fc (+ activation), fused_fc_elementwise_layernorm, skip_layernorm,
@@ -30,41 +30,8 @@
 #include <string>
 #include <tuple>
 
-#include "../kernels/fa_args.h"
+#include "../kernels/piamd_kernels.h"
 #include "kernels.h"
-
-extern "C" {
-int piamd_agemm_load(const char* path);
-int piamd_agemm(const void* a, long long lda, int trans_a, const void* b, long long ldb, int trans_b,
-                void* c, long long ldc, int c_f32, int accumulate, int M, int N, int K, int epi, int act,
-                const void* bias, void* aux, long long ldaux, int ksplit, void* ws, int f16, int batch,
-                long long sa, long long sb, long long sc, hipStream_t st);
-int piamd_small_gemm(int f16, const void* a, long long lda, const void* b, long long ldb, void* c,
-                     long long ldc, int c_f32, int M, int N, int K, int mb, int nb, int wn, int depth,
-                     int ks, float alpha, const void* bias, int act, const void* resid, long long ldr,
-                     float* ws, int* cnt, hipStream_t st);
-int piamd_bias_act_fwd(int f16, int act, const void* x, const void* bias, void* y, void* pre, long long n,
-                       int N, hipStream_t stream);
-int piamd_layernorm_fwd(int dtype, const void* x, const void* bias, const void* residual, const void* gamma,
-                        const void* beta, void* y, void* residual_out, float* mean, float* rstd, int rows,
-                        int N, float eps, float p_drop, uint64_t seed, uint64_t offset, int flags,
-                        hipStream_t stream);
-int piamd_fa_fwd(const FaArgs* args, int f16, hipStream_t stream);
-int piamd_embedding_fwd(const long long* ids, const void* w, long long start, int vlocal, const void* p,
-                        const long long* pos, int S, void* out, long long T, int H, hipStream_t st);
-int piamd_transpose_bf16(const void* src, void* dst, int R, int C, hipStream_t stream);
-int piamd_softmax_fwd(int f16, const void* x, const void* mask, int mask_rows, int causal_q, void* y,
-                      int rows, int N, float scale, hipStream_t stream);
-int piamd_qkv_prep(void* qkv, long long ld, const void* bias, void* kc, void* vc, const int* pos0, int B, int S,
-                   int Hq, int Hk, int D, int maxS, int rot, int neox, float base, hipStream_t st);
-int piamd_decode_attn(const void* qkv, long long ldq, const void* bias, int prep, int rot, int neox, float base,
-                      void* kc, void* vc, const int* lens, int B, int Hq, int Hk, int D, int maxS, int chunk,
-                      int nsplit, const void* mask, long long ldm, float scale, float* part, int* cnt, void* out,
-                      long long ldo, hipStream_t st);
-int piamd_wo_gemm_ex(int bits, const void* x, long long ldx, const void* wp, const float* scale, const void* bias,
-                     void* y, long long ldy, float* ws, int* cnt, int M, int N, int K, int KS, int act,
-                     const void* ln_g, const void* ln_b, float eps, const void* resid, long long ldr, hipStream_t st);
-}
 
 #define FCHK(call, what)                                                                      \
   do {                                                                                        \
@@ -235,7 +202,8 @@ void gemm_nt(Ctx& c, int f16, const void* a, int64_t lda, const void* b, int64_t
       cnt = (int*)st.sg_cnt->p;
     }
     FCHK(piamd_small_gemm(f16, a, lda, b, ldb, out, ldc, 0, M, N, K, g.mb, g.nb, g.wn, g.depth, g.ks, 1.f,
-                          bias, act, nullptr, 0, ws, cnt, S(c)),
+                          bias, act, nullptr, 0, ws, cnt, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr,
+                          nullptr, S(c)),
          who + " (skinny GEMM)");
     return;
   }
@@ -247,7 +215,7 @@ void gemm_nt(Ctx& c, int f16, const void* a, int64_t lda, const void* b, int64_t
                      (bias || act != A_NONE);
   if (fused) {
     FCHK(piamd_agemm(a, lda, 0, b, ldb, 1, out, ldc, 0, 0, M, N, K, 1, act, bias, nullptr, 0, 1, nullptr, f16,
-                     1, 0, 0, 1, S(c)),
+                     1, 0, 0, 1, nullptr, S(c)),
          who + " (assembly GEMM)");
     return;
   }
@@ -261,7 +229,7 @@ void gemm_nt(Ctx& c, int f16, const void* a, int64_t lda, const void* b, int64_t
     ws = st.ks_ws->p;
   }
   FCHK(piamd_agemm(a, lda, 0, b, ldb, 1, out, ldc, 0, 0, M, N, K, 0, 0, nullptr, nullptr, 0, ks, ws, f16, 1,
-                   0, 0, 1, S(c)),
+                   0, 0, 1, nullptr, S(c)),
        who + " (assembly GEMM)");
   if (bias || act != A_NONE) {
     if (ldc != N) throw std::runtime_error(who + ": strided output with an unfused epilogue");
@@ -288,7 +256,7 @@ DTensor transposed(Ctx& c, const DTensor& w, const std::string& who) {
   if (w.dims.size() != 2) throw std::runtime_error(who + ": weight must be 2-D");
   const int R = (int)w.dims[0], C = (int)w.dims[1];
   DTensor t = make(c, w.dtype, {w.dims[1], w.dims[0]});
-  FCHK(piamd_transpose_bf16(w.buf->p, t.buf->p, R, C, S(c)), who + " (transpose)");
+  FCHK(piamd_bf16_transpose(w.buf->p, t.buf->p, R, C, S(c)), who + " (transpose)");
   if (!cache) return t;
   keep_persistent(c, t);
   return st.wt[w.buf->p] = t;
@@ -441,7 +409,8 @@ void op_lookup(Ctx& c, const OpDesc& op, Scope& s) {
   const int64_t H = w.dims[1];
   od.push_back(H);
   DTensor o = make(c, w.dtype, od);
-  FCHK(piamd_embedding_fwd((const long long*)ids.buf->p, w.buf->p, 0, (int)w.dims[0], nullptr, nullptr, 1,
+  // dtype code 1: the 16-bit row gather (no position table is added)
+  FCHK(piamd_embedding_fwd(1, (const long long*)ids.buf->p, w.buf->p, 0, (int)w.dims[0], nullptr, nullptr, 1,
                            o.buf->p, ids.numel(), (int)H, S(c)),
        "lookup_table_v2");
   s[op.out("Out")] = o;
@@ -460,7 +429,7 @@ void op_emb_eltwise_ln(Ctx& c, const OpDesc& op, Scope& s) {
     if (!od.empty() && od.back() == 1) od.pop_back();
     od.push_back(w.dims[1]);
     DTensor e = make(c, w.dtype, od);
-    FCHK(piamd_embedding_fwd((const long long*)ids.buf->p, w.buf->p, 0, (int)w.dims[0], nullptr, nullptr, 1,
+    FCHK(piamd_embedding_fwd(1, (const long long*)ids.buf->p, w.buf->p, 0, (int)w.dims[0], nullptr, nullptr, 1,
                              e.buf->p, ids.numel(), (int)w.dims[1], S(c)),
          "fused_embedding_eltwise_layernorm");
     if (i == 0) {
@@ -609,9 +578,9 @@ DTensor fmt_gemv(Ctx& c, const DTensor& x, int M, int K, const DTensor& wp, int 
       ws = (float*)zscratch(c, "wo_ks" + k + "x" + std::to_string(KS), (size_t)KS * M * N * 4);
     }
   }
-  FCHK(piamd_wo_gemm_ex(16, xin, K, wp.buf->p, nullptr, bias ? bias->buf->p : nullptr, y.buf->p, N, ws, cnt, M, N,
-                        K, KS, act, fuse_ln ? lng->buf->p : nullptr, fuse_ln ? lnb->buf->p : nullptr, eps,
-                        resid ? resid->buf->p : nullptr, resid ? N : 0, S(c)),
+  FCHK(piamd_wo_gemm(16, xin, K, wp.buf->p, nullptr, bias ? bias->buf->p : nullptr, y.buf->p, N, ws, cnt, M, N,
+                     K, KS, act, fuse_ln ? lng->buf->p : nullptr, fuse_ln ? lnb->buf->p : nullptr, eps,
+                     resid ? resid->buf->p : nullptr, resid ? N : 0, S(c)),
        who + " (weight-stream GEMV)");
   return y;
 }

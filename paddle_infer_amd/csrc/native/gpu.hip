@@ -11,12 +11,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../kernels/piamd_kernels.h"
 #include "kernels.h"
-
-extern "C" int piamd_layernorm_fwd(int dtype, const void* x, const void* bias, const void* residual,
-                                   const void* gamma, const void* beta, void* y, void* residual_out,
-                                   float* mean, float* rstd, int rows, int N, float eps, float p_drop,
-                                   uint64_t seed, uint64_t offset, int flags, hipStream_t stream);
 
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \

@@ -95,7 +95,7 @@ def eligible(gen, B: int) -> bool:
             t = spec.get(key)
             if t is None or t.dtype != torch.bfloat16:
                 return False
-    return (_lib.available() and _lib.has("piamd_decode_mega_batch_supported")
+    return (_lib.available()
             and _lib.lib().piamd_decode_mega_batch_supported(E_, D_, hq, hk, F_, rot, w8, B) == 1)
 
 
@@ -196,7 +196,7 @@ class MegaDecoder:
         if not self._variant_ok(self.mm):
             self.mm = 1 - self.mm
         # greedy tail (decode_head_kernel): LM head + argmax + bookkeeping + next embedding
-        self.head_ok = nb == 1 and _lib.has("piamd_decode_head_greedy") and self._head_tables(gen)
+        self.head_ok = nb == 1 and self._head_tables(gen)
         self.best = torch.zeros(8 * 32, dtype=torch.int64, device=dev)
         self.cnt = torch.zeros(9 * 64, dtype=torch.int32, device=dev)
 

@@ -142,7 +142,7 @@ class _BNAct(torch.autograd.Function):
         # statistics the conv forward left on its output (ops/conv.py BN_STATS): finalize those
         # instead of a statistics pass over x
         part, P = _conv_stats(x, training, nhwc, C)
-        _lib.call("piamd_bn_fwd3", int(x.dtype == torch.bfloat16), int(nhwc), xc.data_ptr(),
+        _lib.call("piamd_bn_fwd", int(x.dtype == torch.bfloat16), int(nhwc), xc.data_ptr(),
                   _lib.ptr(res), y.data_ptr(), N, C, S, _lib.ptr(g), _lib.ptr(b), _lib.ptr(rm),
                   _lib.ptr(rv), mean.data_ptr(), rstd.data_ptr(), float(momentum), float(eps),
                   int(training), int(act), ws.data_ptr(), _lib.ptr(ss), _lib.ptr(part), P,
@@ -165,7 +165,7 @@ class _BNAct(torch.autograd.Function):
         dg = torch.empty(C, device=xc.device, dtype=torch.float32)
         db = torch.empty(C, device=xc.device, dtype=torch.float32)
         ws = torch.empty(3 * C + 2 * _MAX_PARTS * C, device=xc.device, dtype=torch.float32)
-        _lib.call("piamd_bn_bwd2", int(xc.dtype == torch.bfloat16), int(nhwc), dyc.data_ptr(),
+        _lib.call("piamd_bn_bwd", int(xc.dtype == torch.bfloat16), int(nhwc), dyc.data_ptr(),
                   y.data_ptr(), xc.data_ptr(), dx.data_ptr(), _lib.ptr(dres), N, C, S, _lib.ptr(g),
                   mean.data_ptr(), rstd.data_ptr(), dg.data_ptr(), db.data_ptr(), int(training),
                   int(act), ws.data_ptr(), _lib.ptr(ss), _lib.stream())
@@ -223,7 +223,7 @@ def _welford_merge(g):
 
 class _SyncBN(torch.autograd.Function):
     """Cross-rank batch norm: Welford (count, mean, M2) triples all-gathered over ``group`` and
-    merged (GPU: inside ``piamd_bn_fwd3`` as channel-major partials), backward sums all-reduced.
+    merged (GPU: inside ``piamd_bn_fwd`` as channel-major partials), backward sums all-reduced.
     Reference `phi/kernels/gpu/sync_batch_norm_kernel.cu:192` (dγ / dβ are the local sums, like
     the reference's KeBNBackwardScaleBias; the data-parallel gradient reduction sums them)."""
 
@@ -261,7 +261,7 @@ class _SyncBN(torch.autograd.Function):
             gb = bias.float().contiguous() if bias is not None else None
             rm = running_mean if running_mean is not None and running_mean.dtype == torch.float32 else None
             rv = running_var if running_var is not None and running_var.dtype == torch.float32 else None
-            _lib.call("piamd_bn_fwd3", int(x.dtype == torch.bfloat16), int(nhwc), xc.data_ptr(), None,
+            _lib.call("piamd_bn_fwd", int(x.dtype == torch.bfloat16), int(nhwc), xc.data_ptr(), None,
                       y.data_ptr(), N, C, S, _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(rm), _lib.ptr(rv),
                       mean.data_ptr(), rstd.data_ptr(), float(momentum), float(eps), 1, 0,
                       ws.data_ptr(), None, part_t.data_ptr(), part_t.shape[-1], _lib.stream())

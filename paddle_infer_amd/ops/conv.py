@@ -123,10 +123,10 @@ def _launch(x, w_ohwi, bias, st, pad, dil, act, rs=None, out_f32=False, stats_ou
     def run(plan, stats=None):
         tn, ks = plan
         ws = torch.empty(ks * M * K, dtype=torch.float32, device=x.device) if ks > 1 else None
-        _lib.call("piamd_conv2d_fwd2", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
+        _lib.call("piamd_conv2d_fwd", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
                   y.data_ptr(), N, H, W, C, OH, OW, R, S, st[0], st[1], pad[0], pad[1], dil[0],
                   dil[1], K, act, _lib.ptr(b), tn, ks, _lib.ptr(ws), flags, _lib.ptr(stats),
-                  _lib.stream())
+                  0, 0, 0, 0, 0, 0, _lib.stream())
     plan = PLAN_OVERRIDE or _autotuned("conv2d_fwd", (N, H, W, C, K, R, S, st, pad, dil, act)
                                        + (("f32",) if out_f32 else ()),
                                        _plan(M, K, nk), _fwd_candidates(M, K, nk), run)
@@ -331,7 +331,7 @@ def _launch_geom(x, w_ohwi, st, pad, dil, OH, OW, out_f32=False, out=None, phase
             if not scratch:
                 scratch.append(torch.empty(N, OH, OW, K, dtype=dt, device=x.device))
             ws = torch.empty(ks_ * M * K, dtype=torch.float32, device=x.device) if ks_ > 1 else None
-            _lib.call("piamd_conv2d_fwd3", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
+            _lib.call("piamd_conv2d_fwd", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
                       scratch[0].data_ptr(), N, H, W, C, OH, OW, R, S, st[0], st[1], pad[0], pad[1],
                       dil[0], dil[1], K, 0, 0, tn_, ks_, _lib.ptr(ws), flags, None, 0, 0, 0, 0, 0, 0,
                       _lib.stream())
@@ -340,7 +340,7 @@ def _launch_geom(x, w_ohwi, st, pad, dil, OH, OW, out_f32=False, out=None, phase
         if ks != 1:
             acc += _launch_geom(x, w_ohwi, st, pad, dil, OH, OW)
             return acc
-        _lib.call("piamd_conv2d_fwd3", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
+        _lib.call("piamd_conv2d_fwd", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
                   acc.data_ptr(), N, H, W, C, OH, OW, R, S, st[0], st[1], pad[0], pad[1], dil[0],
                   dil[1], K, 0, 0, tn, 1, None, flags | 4, None, 0, 0, 0, 0, 0, 0, _lib.stream())
         return acc
@@ -354,7 +354,7 @@ def _launch_geom(x, w_ohwi, st, pad, dil, OH, OW, out_f32=False, out=None, phase
             y = torch.empty(N, OH, OW, K, dtype=dt, device=x.device)
         dst = out if direct else y
         geo = (out.shape[1], out.shape[2]) + tuple(phase) if direct else (0, 0, 0, 0, 0, 0)
-        _lib.call("piamd_conv2d_fwd3", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
+        _lib.call("piamd_conv2d_fwd", x.data_ptr(), w_ohwi.data_ptr(), _zero(x.device).data_ptr(),
                   dst.data_ptr(), N, H, W, C, OH, OW, R, S, st[0], st[1], pad[0], pad[1], dil[0],
                   dil[1], K, 0, 0, tn, ks, _lib.ptr(ws), flags, None, *geo, _lib.stream())
         if out is not None and not direct:
@@ -617,7 +617,7 @@ WPREP = os.environ.get("PIAMD_CONV_WPREP", "1") != "0"
 def _wprep_ok(x, weight):
     """One-launch filter preparation (``conv_wprep.hip``) for this conv's weight."""
     return (WPREP and x.is_cuda and weight.is_cuda and weight.dim() == 4 and weight.dtype in _WSRC
-            and x.dtype in (torch.bfloat16, torch.float16) and _lib.has("piamd_conv_wprep"))
+            and x.dtype in (torch.bfloat16, torch.float16))
 
 
 # ------------------------------------------------------------------------- dense fp32 (split bf16)

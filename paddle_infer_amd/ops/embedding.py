@@ -48,7 +48,7 @@ class _Embedding(torch.autograd.Function):
         S = shp[-1] if len(shp) > 1 else T
         out = torch.empty((T, H), dtype=w.dtype, device=w.device)
         pf = None if pos_ids is None else pos_ids.reshape(-1).contiguous().long()
-        _lib.call("piamd_embedding_fwd", idf.data_ptr(), w.data_ptr(), start, w.shape[0],
+        _lib.call("piamd_embedding_fwd", 1, idf.data_ptr(), w.data_ptr(), start, w.shape[0],
                   _lib.ptr(pos_table), _lib.ptr(pf), S, out.data_ptr(), T, H, _lib.stream())
         ctx.save_for_backward(idf, pf)
         ctx.w, ctx.pt = w, pos_table
@@ -115,7 +115,7 @@ class _Lookup(torch.autograd.Function):
         idf = ids.reshape(-1).contiguous()
         T = idf.numel()
         out = torch.empty((T, H), dtype=w.dtype, device=w.device)
-        _lib.call("piamd_embedding_fwd_dt", _DT[w.dtype], idf.data_ptr(), w.data_ptr(), 0, w.shape[0],
+        _lib.call("piamd_embedding_fwd", _DT[w.dtype], idf.data_ptr(), w.data_ptr(), 0, w.shape[0],
                   None, None, 1, out.data_ptr(), T, H, _lib.stream())
         ctx.save_for_backward(idf)
         ctx.w = w

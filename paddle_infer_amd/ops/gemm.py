@@ -113,17 +113,11 @@ def asm_gemm(a, b, trans_a=False, trans_b=False, out=None, out_f32=False, accumu
     if colsum is not None:
         assert epi == "dact" and colsum.dtype == torch.float32 and colsum.is_contiguous() \
             and tuple(colsum.shape) == ((M + 127) // 128, N)
-        _lib.call("piamd_agemm2", a.data_ptr(), a.stride(-2), int(trans_a), b.data_ptr(), b.stride(-2),
-                  int(trans_b), out.data_ptr(), out.stride(-2), int(out.dtype == torch.float32),
-                  int(accumulate), M, N, K, _EPI[epi], ACTS[act], _lib.ptr(bias), _lib.ptr(aux),
-                  aux.stride(0) if aux is not None else 0, ksplit, _lib.ptr(ws), int(f16), nb,
-                  sa, sb, max(sc, 1), colsum.data_ptr(), _lib.stream())
-        return out
     _lib.call("piamd_agemm", a.data_ptr(), a.stride(-2), int(trans_a), b.data_ptr(), b.stride(-2),
               int(trans_b), out.data_ptr(), out.stride(-2), int(out.dtype == torch.float32),
               int(accumulate), M, N, K, _EPI[epi], ACTS[act], _lib.ptr(bias), _lib.ptr(aux),
               aux.stride(0) if aux is not None else 0, ksplit, _lib.ptr(ws), int(f16), nb,
-              sa, sb, max(sc, 1), _lib.stream())
+              sa, sb, max(sc, 1), _lib.ptr(colsum), _lib.stream())
     return out
 
 
@@ -253,11 +247,24 @@ def small_gemm(a, b, out=None, out_f32=False, alpha=1.0, bias=None, act="none", 
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32 if out_f32 else half, device=a.device)
     mb, nb, wn, depth, ks = cfg or small_cfg(M, N, K)
+    assert not slices or (ln is None and resid_ln is None), "slices: no LayerNorm arguments"
     if ln is not None or resid_ln is not None:
-        if ln is not None:
-            ks = 1
-        return _small_gemm_ln(a, b, out, M, N, K, (mb, nb, wn, depth, ks), act, resid, ln, ln_stats,
-                              resid_ln, bias, alpha)
+        assert a.dtype == b.dtype and a.dtype in _HALF, "LayerNorm fold: bf16 / fp16 operands of one dtype"
+    c1 = b2 = rs = rg = rb = None
+    eps = 0.0
+    if ln is not None:
+        c1, b2, eps = ln
+        assert c1.dtype == torch.float32 and b2.dtype == torch.float32 and c1.numel() == N == b2.numel()
+        if not (depth >> 4 in (2, 4) and depth & 15 == 1 and wn == 1):  # LN fold: one ring depth, or B 2 / 4 deep
+            depth &= 15
+        ks, bias, alpha = 1, None, 1.0
+    if ln_stats is not None:
+        assert ln is not None and ln_stats.dtype == torch.float32 and ln_stats.numel() >= 2 * M
+    if resid_ln is not None:
+        rs, rg, rb = resid_ln
+        assert resid is not None and rs.dtype == torch.float32 and rs.numel() >= 2 * M
+        assert rg.dtype == a.dtype and rb.dtype == a.dtype and rg.numel() == N == rb.numel()
+        rg, rb = rg.contiguous(), rb.contiguous()
     ws = cnt = None
     if ks > 1:
         if slices:
@@ -266,10 +273,11 @@ def small_gemm(a, b, out=None, out_f32=False, alpha=1.0, bias=None, act="none", 
             tiles = -(-M // (16 * mb)) * -(-N // (16 * nb * wn))
             ws, cnt = _sg_fixup_bufs(a.device, M, N, tiles)
     _lib.call("piamd_small_gemm", int(half == torch.float16), a.data_ptr(), a.stride(0),
-              b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0),
-              int(out.dtype == torch.float32), M, N, K, mb, nb, wn, depth, ks, float(alpha), _lib.ptr(bias),
-              _SG_ACTS[act], _lib.ptr(resid), resid.stride(0) if resid is not None else 0,
-              _lib.ptr(ws), _lib.ptr(cnt), _lib.stream())
+              b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), int(out.dtype == torch.float32),
+              M, N, K, mb, nb, wn, depth, ks, float(alpha), _lib.ptr(bias), _SG_ACTS[act], _lib.ptr(resid),
+              resid.stride(0) if resid is not None else 0, _lib.ptr(ws), _lib.ptr(cnt), _lib.ptr(c1),
+              _lib.ptr(b2), float(eps), _lib.ptr(ln_stats), _lib.ptr(rs), _lib.ptr(rg), _lib.ptr(rb),
+              _lib.stream())
     return out
 
 
@@ -285,39 +293,6 @@ def ln_fold(w_nk, gamma, beta, bias=None):
     return wf, c1, b2.contiguous()
 
 
-def _small_gemm_ln(a, b, out, M, N, K, cfg, act, resid, ln, ln_stats=None, resid_ln=None, bias=None,
-                   alpha=1.0):
-    assert a.dtype == b.dtype and a.dtype in _HALF, "LayerNorm fold: bf16 / fp16 operands of one dtype"
-    mb, nb, wn, depth, ks = cfg
-    c1 = b2 = None
-    eps = 0.0
-    if ln is not None:
-        c1, b2, eps = ln
-        assert c1.dtype == torch.float32 and b2.dtype == torch.float32 and c1.numel() == N == b2.numel()
-        if not (depth >> 4 in (2, 4) and depth & 15 == 1 and wn == 1):  # LN fold: one ring depth, or B 2 / 4 deep
-            depth &= 15
-        ks, bias, alpha = 1, None, 1.0
-    if ln_stats is not None:
-        assert ln is not None and ln_stats.dtype == torch.float32 and ln_stats.numel() >= 2 * M
-    rs = rg = rb = None
-    if resid_ln is not None:
-        rs, rg, rb = resid_ln
-        assert resid is not None and rs.dtype == torch.float32 and rs.numel() >= 2 * M
-        assert rg.dtype == a.dtype and rb.dtype == a.dtype and rg.numel() == N == rb.numel()
-        rg, rb = rg.contiguous(), rb.contiguous()
-    ws = cnt = None
-    if ks > 1:
-        tiles = -(-M // (16 * mb)) * -(-N // (16 * nb * wn))
-        ws, cnt = _sg_fixup_bufs(a.device, M, N, tiles)
-    _lib.call("piamd_small_gemm_ln", int(a.dtype == torch.float16), a.data_ptr(), a.stride(0),
-              b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), int(out.dtype == torch.float32),
-              M, N, K, mb, nb, wn, depth, ks, float(alpha), _lib.ptr(bias), _SG_ACTS[act], _lib.ptr(resid),
-              resid.stride(0) if resid is not None else 0, _lib.ptr(ws), _lib.ptr(cnt), _lib.ptr(c1),
-              _lib.ptr(b2), float(eps), _lib.ptr(ln_stats), _lib.ptr(rs), _lib.ptr(rg), _lib.ptr(rb),
-              _lib.stream())
-    return out
-
-
 def own_dtype(*ts):
     """The own GEMMs take bf16 / fp16 CUDA operands of one dtype."""
     t0 = ts[0]
@@ -330,7 +305,7 @@ def own_dtype(*ts):
 # products run as ONE bf16 MFMA GEMM over a 3×-long reduction ([x_hi | x_lo | x_hi] ·
 # [w_hi | w_hi | w_lo]) with an f32 result: ≈2^-16 relative per product, at 3× the bf16 work —
 # still ≈3× the f32 MFMA rate (`MI355X_MICROARCH.md` § Matrix cores: f32-input MFMA = 1/16 bf16).
-# The operand split is one HIP pass (`piamd_split3_f32`).
+# The operand split is one HIP pass (`piamd_f32_split_hilo`).
 # ---------------------------------------------------------------------------------------------
 FP32_SPLIT = True  # False: fp32 GEMMs on the library (exact fp32)
 _LO = {"hlh": 0b010, "hhl": 0b100}
@@ -356,7 +331,7 @@ def split3(t, order, axis=0, Rp=None, Cp=None):
         Cp = C
         assert C % 8 == 0, "row-stacked split needs C % 8 == 0"
         out = torch.empty((3 * Rp, C), dtype=torch.bfloat16, device=t.device)
-    _lib.call("piamd_split3_f32", t.data_ptr(), t.stride(0) if R > 1 else C, out.data_ptr(), R, C, Rp, Cp,
+    _lib.call("piamd_f32_split_hilo", t.data_ptr(), t.stride(0) if R > 1 else C, out.data_ptr(), R, C, Rp, Cp,
               _LO[order], axis, _lib.stream())
     return out
 

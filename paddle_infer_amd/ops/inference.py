@@ -217,7 +217,7 @@ def ln_fusable(M, K, KS=1):
 
 def _wo_call(bits, x2, w, scale, bias, y, M, N, K, KS, act, ln, resid, ws, cnt):
     lg, lb, eps = ln if ln is not None else (None, None, 0.0)
-    _lib.call("piamd_wo_gemm_ex", bits, x2.data_ptr(), x2.stride(0), w.data_ptr(), _lib.ptr(scale),
+    _lib.call("piamd_wo_gemm", bits, x2.data_ptr(), x2.stride(0), w.data_ptr(), _lib.ptr(scale),
               _lib.ptr(bias), y.data_ptr(), y.stride(0), _lib.ptr(ws), _lib.ptr(cnt), M, N, K, KS,
               act, _lib.ptr(lg), _lib.ptr(lb), float(eps), _lib.ptr(resid),
               resid.stride(0) if resid is not None else 0, _lib.stream())
@@ -382,7 +382,7 @@ def weight_only_linear(x, weight, bias=None, weight_scale=None, weight_dtype="in
         ws, cnt = _splitk_bufs(x.device, KS, M, N, tiles)
         _lib.call("piamd_wo_gemm", bits, x2.data_ptr(), x2.stride(0), weight.data_ptr(),
                   scale.data_ptr(), _lib.ptr(bias), y.data_ptr(), y.stride(0), _lib.ptr(ws),
-                  _lib.ptr(cnt), M, N, K, KS, act, _lib.stream())
+                  _lib.ptr(cnt), M, N, K, KS, act, None, None, 0.0, None, 0, _lib.stream())
         return y.reshape(*lead, N)
     w = _unpack(weight, bits, N, K).float() * weight_scale.float()[:, None]
     y = x2.float() @ w.t()
@@ -430,7 +430,7 @@ def int8_gemm(xq, xs, wq, ws, bias=None, act="none"):
     assert K % 128 == 0 and N % 4 == 0, "int8 GEMM needs K % 128 == 0 and N % 4 == 0"
     y = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
     wsf = ws.float().contiguous()
-    _lib.call("piamd_gemm_i8", xq.data_ptr(), xq.stride(0), wq.data_ptr(), wq.stride(0),
+    _lib.call("piamd_int8_gemm", xq.data_ptr(), xq.stride(0), wq.data_ptr(), wq.stride(0),
               xs.data_ptr(), 0.0, wsf.data_ptr(), _lib.ptr(bias), y.data_ptr(), y.stride(0), M, N,
               K, ACTS[act], _lib.stream())
     return y

@@ -126,7 +126,7 @@ def transposed(w):
     buf.__dict__.pop("_piamd_pad", None)  # ... which this rewrite (no version bump) invalidates
     if R % 8 == 0 and C % 8 == 0:
         from . import _lib
-        _lib.call("piamd_transpose_bf16", w.data_ptr(), buf.data_ptr(), R, C, _lib.stream())
+        _lib.call("piamd_bf16_transpose", w.data_ptr(), buf.data_ptr(), R, C, _lib.stream())
     else:
         buf.copy_(w.detach().t())
     w._piamd_t = (key, buf)

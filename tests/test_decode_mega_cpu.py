@@ -24,7 +24,7 @@ def test_not_eligible_off_gpu_or_off_shape(monkeypatch):
 def test_megaargs_mirror_matches_kernel_struct():
     from paddle_infer_amd.ops import _lib
     src = open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", "kernels",
-                            "decode_mega.hip")).read()
+                            "decode_args.h")).read()
     body = src[src.index("struct MegaArgs {"):]
     body = body[:body.index("};")]
     body = re.sub(r"//[^\n]*", "", body)
@@ -36,7 +36,7 @@ def test_headargs_mirror_matches_kernel_struct():
     import ctypes
     from paddle_infer_amd.ops import _lib
     src = open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", "kernels",
-                            "decode_mega.hip")).read()
+                            "decode_args.h")).read()
     body = src[src.index("struct HeadArgs {") + len("struct HeadArgs {"):]
     body = re.sub(r"//[^\n]*", "", body[:body.index("};")])
     names = [re.findall(r"\w+", part)[-1] for stmt in body.split(";") if stmt.strip()

@@ -1,6 +1,6 @@
 """Numerics model of the fp32 split-bf16 GEMM (`ops/gemm.py gemm_nt_f32`): x·w ≈ x_hi·w_hi +
 x_lo·w_hi + x_hi·w_lo with t = bf16(t) + bf16(t − bf16(t)), emulated on the CPU exactly as the
-kernel forms its operands (`piamd_split3_f32`), against fp64 — the bound the GPU tests assert."""
+kernel forms its operands (`piamd_f32_split_hilo`), against fp64 — the bound the GPU tests assert."""
 import pytest
 import torch
 

@@ -19,7 +19,7 @@ def test_transpose_bf16(R, C):
     from paddle_infer_amd.ops import _lib
     w = torch.randn(R, C, device=DEV).bfloat16()
     out = torch.empty(C, R, device=DEV, dtype=torch.bfloat16)
-    _lib.call("piamd_transpose_bf16", w.data_ptr(), out.data_ptr(), R, C, _lib.stream())
+    _lib.call("piamd_bf16_transpose", w.data_ptr(), out.data_ptr(), R, C, _lib.stream())
     assert torch.equal(out, w.t())
 
 
@@ -41,6 +41,6 @@ def test_linear_transposed_weight_cache():
         ptr = w.data_ptr()
         tmp = (w.float() * 0.5).bfloat16()
         from paddle_infer_amd.ops import _lib
-        _lib.call("piamd_transpose_bf16", tmp.t().contiguous().data_ptr(), ptr, 512, 256, _lib.stream())
+        _lib.call("piamd_bf16_transpose", tmp.t().contiguous().data_ptr(), ptr, 512, 256, _lib.stream())
     L.bump_param_epoch()
     _close(L.linear(x, w, b), x.float() @ tmp.float(), 0.02)

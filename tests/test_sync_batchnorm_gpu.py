@@ -1,4 +1,4 @@
-"""SyncBatchNorm's GPU kernels (`batchnorm.hip` piamd_bn_local_stats / piamd_bn_fwd3 with
+"""SyncBatchNorm's GPU kernels (`batchnorm.hip` piamd_bn_local_stats / piamd_bn_fwd with
 cross-rank partials / piamd_bn_bwd_local_sums / piamd_bn_bwd_apply_sums) at world size 1 against
 the fp32 PyTorch batch norm: statistics, output, input / affine gradients, running stats."""
 import pytest
